@@ -16,6 +16,13 @@ k_merge_bucket x4, k_merge_long*, k_tile_count + scan, k_compact, k_string_offse
 Prints ONE JSON line (rank 0).  Launch for N>1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
       --master-port P bench.py --gpus N
+
+A plain run builds the batch, warms up, times the steps and prints the line (the roofline figures
+come from HIP events inside the timed steps).  --full adds the legs that take runs of their own:
+the chunk count, the checks against the host finder and of the reassembly, the small-batch
+latencies, the PCIe-inclusive rate, and the CPU baseline with the parity spot-check; their fields
+are null without it.  --dump-outputs DIR writes what the last timed step computed (see
+dump_outputs).
 """
 import argparse
 import ctypes
@@ -45,6 +52,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: chunk count, finder and reassembly checks, "
+                         "small-batch latencies (--small-steps), PCIe-inclusive rate (--e2e-steps), CPU baseline "
+                         "and parity spot-check (--no-cpu-baseline: without)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--config", default="c3", choices=["c3", "c5"],
                     help="c3: 1 GiB MIXED + 32k merges (configs[1]/[2]); c5: stress, 50k merges")
     ap.add_argument("--corpus", default=None, choices=["mixed", "stress", "entropy", "ascii"],
@@ -72,10 +85,10 @@ def parse():
     ap.add_argument("--cpu-sample-mb", type=float, default=320.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--small-steps", type=int, default=20,
-                    help="rank 0, N=1: per-call latency of ~64 KiB and ~1 MiB prefixes through the same handle after "
-                         "the big launches (0: skip)")
+                    help="--full, rank 0, N=1: per-call latency of ~64 KiB and ~1 MiB prefixes through the same handle "
+                         "after the big launches (0: skip)")
     ap.add_argument("--e2e-steps", type=int, default=2,
-                    help="N=1: also time host buffers -> host buffers (PCIe-inclusive, reported beside value)")
+                    help="--full, N=1: also time host buffers -> host buffers (PCIe-inclusive, reported beside value)")
     ap.add_argument("--threads", type=int, default=0,
                     help="host threads for corpus/pre-split and the all-cores CPU baseline (0: every usable core)")
     ap.add_argument("--no-dedupe", action="store_true",
@@ -114,6 +127,45 @@ def host_cpu():
     except OSError:
         pass
     return usable, os.cpu_count(), model
+
+
+DUMP_STRINGS = 4096       # strings whose ids are written in full (a fixed, seeded choice)
+DUMP_IDS_MAX = 4 << 20    # ids written at most (16 MB as float32)
+DUMP_OFF_MAX = 2 << 20    # offsets written at most (16 MB as float64, and as much for their indices)
+
+
+def dump_outputs(path, d_ids, d_off, n_strings):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the batch's ids
+    (d_ids, device, any integer width) and its n_strings + 1 string offsets into them (d_off) -- as
+    .npy files under `path`, a few tens of MB whatever the batch:
+      offsets.npy     float64: every offset (exact below 2^53), or, past DUMP_OFF_MAX of them, those
+                      at offset_index.npy
+      strings.npy     float64: a seeded choice of DUMP_STRINGS strings, ascending; it depends on the
+                      number of strings alone, so two builds given the same arguments choose alike
+      ids_sample.npy  float32 (ids are below 2^24): the ids of those strings one after another, cut
+                      at DUMP_IDS_MAX
+      counts.npy      float64: [strings, ids in the batch]"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20240229)
+    off = d_off[:n_strings + 1].cpu().numpy().astype(np.int64)
+    pick = np.sort(rng.choice(n_strings, size=min(DUMP_STRINGS, n_strings), replace=False))
+    idx = np.concatenate([np.arange(off[s], off[s + 1]) for s in pick] or [np.zeros(0, np.int64)])[:DUMP_IDS_MAX]
+    if len(idx) and not (0 <= int(idx.min()) and int(idx.max()) < d_ids.numel()):
+        raise SystemExit("--dump-outputs: the offsets point outside the id buffer")
+    ids = d_ids.view(-1)[torch.from_numpy(idx).to(d_ids.device)].cpu().numpy()
+    if ids.dtype == np.int16:  # (16-bit output: an id's low 16 bits)
+        ids = ids.astype(np.int32) & 0xFFFF
+    if len(off) > DUMP_OFF_MAX:
+        at = np.sort(rng.choice(len(off), size=DUMP_OFF_MAX, replace=False))
+        np.save(os.path.join(path, "offset_index.npy"), at.astype(np.float64))
+        off_out = off[at]
+    else:
+        off_out = off
+    np.save(os.path.join(path, "offsets.npy"), off_out.astype(np.float64))
+    np.save(os.path.join(path, "strings.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "ids_sample.npy"), ids.astype(np.float32))
+    np.save(os.path.join(path, "counts.npy"), np.array([n_strings, off[-1]], dtype=np.float64))
 
 
 def main():
@@ -168,7 +220,7 @@ def main():
         raise SystemExit("--specials-device needs the device pre-split (the host pre-split needs host occurrences)")
     t_data = time.time() - t
     t = time.time()
-    if specials:
+    if specials and (args.full or not sp_device):  # (found on the device: the host's only for --full's check)
         sp_host = corpus.find_specials(buf, off, specials, n_threads=args.threads)
     if host_ps:
         bits, n_chunks = (corpus.presplit_specials(buf, off, sp_host[0], sp_host[1], pat, n_threads=args.threads)
@@ -252,7 +304,7 @@ def main():
     def encode(n_tok_ptr=None):
         encode_into(d_out, d_oo, n_tok_ptr)
 
-    if not host_ps and not specials:  # chunk count for the report (outside the timed region)
+    if args.full and not host_ps and not specials:  # chunk count for the report (outside the timed region)
         tmp_bits = torch.empty((n_bytes + 63) // 64, dtype=torch.int64, device=dev)
         c = ctypes.c_int64()
         _lib.check(L.sw_presplit_device(h, d_buf.data_ptr(), n_bytes, d_off.data_ptr(), n_str, pat,
@@ -264,7 +316,7 @@ def main():
     encode(ctypes.byref(n_tok_c))
     n_tok = int(n_tok_c.value)
     sp_dev_ok = None
-    if sp_device:  # (the device finder's occurrences == the host threads', outside the timed region)
+    if args.full and sp_device:  # (the device finder's occurrences == the host threads', outside the timed region)
         nd = int(d_sp[3].item())
         sp_dev_ok = bool(nd == len(sp_host[0]) and np.array_equal(d_sp[0][:nd].cpu().numpy(), sp_host[0])
                          and np.array_equal(d_sp[2][:nd].cpu().numpy(), sp_host[2]))
@@ -364,6 +416,7 @@ def main():
     reassembly_ok = None
     if gather:
         shard.check_bounds()
+    if gather and args.full:
         # the last step's reassembled batch holds this rank's own encode at its displacement, and its
         # offsets end at the batch total
         last = (n_step[0] - 1) % len(outs)
@@ -400,6 +453,12 @@ def main():
     all_bytes, all_tok, all_str, all_chunks = (float(x) for x in totals.tolist())
     ms_step = sec / args.steps * 1e3
     value = all_bytes * args.steps / sec / 1e6
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before any other leg reuses the buffers
+        last = (n_step[0] - 1) % len(outs)
+        if gather:  # (the reassembled batch of every rank's strings)
+            dump_outputs(args.dump_outputs, finals[last][0], finals[last][1], int(all_str))
+        else:
+            dump_outputs(args.dump_outputs, outs[last][0], outs[last][1], n_str)
 
     # roofline of the encode pipeline (all sw_encode_device kernels, HIP events), rank-local, per launch
     # bytes in + ids out + offsets in/out (+ the bitmap when it comes from the host, C3)
@@ -464,7 +523,7 @@ def main():
     # 64 KiB and 1 MiB through the device entry, each call synchronised: the per-call latency a small
     # batch pays (the table clear runs in k_edges only when its grid covers the table)
     small = None
-    if rank == 0 and world == 1 and args.small_steps > 0 and plain and not gather and not host_ps:
+    if args.full and rank == 0 and world == 1 and args.small_steps > 0 and plain and not gather and not host_ps:
         small = {}
         for target in (1 << 16, 1 << 20):
             k = max(1, int(np.searchsorted(off, target, side="right")) - 1)
@@ -489,7 +548,7 @@ def main():
     # the ids and offsets written by the device into the caller's arrays) -- `mb_s`; and plain
     # pageable arrays (staged through the library's pinned buffers by host threads) -- `mb_s_pageable`
     e2e = None
-    if rank == 0 and world == 1 and args.e2e_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.e2e_steps > 0:
         # the caller's output arrays, allocated and touched once (encode_packed(out=...)): a call then
         # writes the ids into resident pages instead of faulting in a fresh 1 GB array
         out_e = np.zeros(n_bytes, dtype=np.int32)
@@ -563,7 +622,7 @@ def main():
     cpu = None
     parity = None
     c1 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # configs[0] (C1): 10 MB synthetic ASCII, the reference-trained 500-merge toy model, CPU only
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
@@ -637,7 +696,7 @@ def main():
                        "dedupe": not args.no_dedupe},
             "mtok_per_s": round(all_tok * args.steps / sec / 1e6, 3),
             "bytes_per_token": round(all_bytes / max(all_tok, 1), 4),
-            "chunks": int(all_chunks),
+            "chunks": int(all_chunks) if n_chunks >= 0 else None,  # (device pre-split: counted by --full)
             "rates": rates,
             "roofline": roofline,
             "cpu_baseline": cpu,
@@ -649,7 +708,9 @@ def main():
             "host_split_s": round(t_split, 3) if (host_ps or specials) else None,
             "host_split_note": ("host threads, outside the timed GPU step: special-token occurrences%s (%d threads)" % (
                 " + %s pre-split bitmap" % args.pattern if host_ps else "", args.threads)) if (host_ps or specials) else None,
-            "specials": ({"per_kib": args.specials, "occurrences": int(len(sp_host[0])), "tokens": SPECIALS,
+            "specials": ({"per_kib": args.specials,
+                          "occurrences": int(len(sp_host[0])) if sp_host is not None else int(d_sp[3].item()),
+                          "tokens": SPECIALS,
                           "end_of_string": "<|endoftext|>", "found": "device" if sp_device else "host",
                           "found_note": ("sw_find_specials_device inside the timed step (its kernels before the "
                                          "encode's; roofline.kernel_ms = the whole step)" if sp_device else

@@ -30,22 +30,22 @@ bench() {  # name args...
   local name=$1; shift
   run "bench_$name" 400 python -u bench.py "$@"
 }
-NB=(--no-cpu-baseline --e2e-steps 0 --small-steps 0)
+NB=(--full --no-cpu-baseline --e2e-steps 0 --small-steps 0)  # (--full: the chunk count and the checks stay in the line)
 for s in "$@"; do
   case $s in
     pytest) run pytest 1100 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
     pytest=*) v=${s#pytest=}; run pytest_part 900 python -u -m pytest ${v//+/ } -x -q --timeout 300 --timeout-method thread ;;
     smoke) run smoke 180 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    c2) bench c2 --steps 20 --warmup 2 ;;
+    c2) bench c2 --full --steps 20 --warmup 2 ;;
     c3) bench c3 --steps 20 --warmup 2 --presplit host "${NB[@]}" ;;
-    c3sp) bench c3sp --steps 20 --warmup 2 --presplit host --pattern gpt2 --specials 1 ;;
-    c3spd) bench c3spd --steps 20 --warmup 2 --pattern gpt2 --specials 1 --specials-device ;;
+    c3sp) bench c3sp --full --steps 20 --warmup 2 --presplit host --pattern gpt2 --specials 1 ;;
+    c3spd) bench c3spd --full --steps 20 --warmup 2 --pattern gpt2 --specials 1 --specials-device ;;
     ent) bench ent --steps 20 --warmup 2 --corpus entropy "${NB[@]}" ;;
     c5) bench c5 --steps 20 --warmup 2 --config c5 "${NB[@]}" ;;
     off) bench off --steps 10 --warmup 2 --no-dedupe --no-chunk-table "${NB[@]}" ;;
     dense) bench dense --steps 10 --warmup 2 --pattern gpt2 --specials 64 --specials-device "${NB[@]}" ;;
     gw1) bench gw1 --steps 10 --warmup 2 --gather-world1 "${NB[@]}" ;;
-    e2e) bench e2e --steps 5 --warmup 2 --no-cpu-baseline --e2e-steps 3 ;;
+    e2e) bench e2e --full --steps 5 --warmup 2 --no-cpu-baseline --e2e-steps 3 ;;
     train) run bench_train 400 python -u tools/bench_train.py --workloads toy500,mixed32m,mixed128m --no-cpu ;;
     prof_c2) run prof_c2 1100 bash tools/profile_gpu.sh "${TAG}_c2" ;;
     prof_c3) run prof_c3 1100 bash tools/profile_gpu.sh "${TAG}_c3" --presplit host ;;
