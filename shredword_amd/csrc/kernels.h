@@ -27,13 +27,12 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "args.h"
 #include "chunktable.h"
 #include "table.h"
 
 namespace sw {
 
-constexpr int kTileBits = 11;
-constexpr int kTile = 1 << kTileBits;        // input bytes per classify workgroup
 constexpr int kThreads = 256;                // 4 waves
 constexpr int kWaves = kThreads / 64;
 // The wave's index in its block as a scalar (readfirstlane): the compiler then keeps the tile
@@ -60,8 +59,6 @@ constexpr int kWin = kTile + 64;             // LDS byte window (tile + halo for
 constexpr int kTileWords = kTile / 64 + 1;   // bitmap words staged (tile + 64-bit halo)
 constexpr int kNumBuckets = 11;              // length buckets of the merge queue
 constexpr int kLongBucket = kNumBuckets - 1;
-constexpr int64_t kRefSpace = 1LL << 30;              // position references below, dense ones above
-constexpr int64_t kMaxLaunchBytes = kRefSpace - 64;   // slot references are int32
 
 // A slot holds a settled token (>= 0) or refers to a merge result:
 //  - slot_ref(p): the result of the chunk starting at position p, res[2p + 1 .. 2p + 1 + res[2p])
@@ -126,40 +123,6 @@ __host__ __device__ inline int bucket_of(int64_t len) {
 }
 __host__ __device__ inline int bucket_min_len(int b) {
   return b <= 2 ? b + 2 : b <= 6 ? 5 + 2 * (b - 3) : b == 7 ? 13 : b == 8 ? 17 : b == 9 ? 25 : 33;
-}
-
-// merges.get((a, b)): the value, or kInf.  Two independent 16-byte loads (both cuckoo
-// candidate buckets), no loop: one memory round trip for every lane.
-template <bool kWide>
-__device__ __forceinline__ uint32_t lookup(const DevTable& t, uint32_t a, uint32_t b) {
-  if (!kWide && t.q16) {  // the quotient table (table.h): one 16-byte bucket, four tagged entries
-    const uint32_t x = q16_mix((a << 16) | b, t.m1, t.m2), tag = x & 0xFFFFu;
-    const uint4 q = ((const uint4*)t.buckets)[x >> t.shift];
-    uint32_t v = 0xFFFFu;
-    v = ((q.x & 0xFFFFu) == tag) ? (q.x >> 16) : v;
-    v = ((q.y & 0xFFFFu) == tag) ? (q.y >> 16) : v;
-    v = ((q.z & 0xFFFFu) == tag) ? (q.z >> 16) : v;
-    v = ((q.w & 0xFFFFu) == tag) ? (q.w >> 16) : v;
-    return (v == 0xFFFFu || (a | b) > 0xFFFFu) ? kInf : v;
-  }
-  const uint32_t f = mix_key(a, b);
-  const uint4* B = (const uint4*)t.buckets;
-  const uint4 q1 = B[bucket1(f, t)];
-  const uint4 q2 = B[bucket2(f, t)];
-  if (!kWide) {
-    const uint32_t key = (a << 16) | b;
-    uint32_t v = kInf;
-    v = (q1.x == key) ? q1.y : v;
-    v = (q1.z == key) ? q1.w : v;
-    v = (q2.x == key) ? q2.y : v;
-    v = (q2.z == key) ? q2.w : v;
-    return ((a | b) > 0xFFFFu) ? kInf : v;
-  } else {
-    uint32_t v = kInf;
-    v = (q1.x == a && q1.y == b) ? q1.z : v;
-    v = (q2.x == a && q2.y == b) ? q2.z : v;
-    return v;
-  }
 }
 
 // Whole-chunk table (chunktable.h): the single token a 2..16-byte chunk encodes to, or kInf if the

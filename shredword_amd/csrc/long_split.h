@@ -59,37 +59,6 @@ constexpr int kLcWords = kLcBig + kLpRounds + 1;
 constexpr int kLcDbg = kLcWords;               // SW_LP_DEBUG builds: per round, big-window bytes (sum, max)
 constexpr int kLcAlloc = kLcWords + 2 * kLpRounds;
 
-struct LongArgs {
-  // the long chunks of the per-chunk wave loop (EncArgs::lstart / llen, count ctl[kLcWave];
-  // SW_OPT_LONG_SPLIT 0 or an ill-formed table)
-  uint32_t* wstart;
-  uint32_t* wlen;
-  // per long chunk of these passes (index i: k_lp_prep's order), lcap of each
-  uint32_t* lstart;  // first byte
-  uint32_t* llen;    // bytes
-  uint32_t* lnp;     // pieces
-  int64_t* lpo;      // exclusive scan of lnp: the chunk's first piece
-  uint32_t* lfall;   // 1: the chunk takes the exact wave loop (k_lp_fallback)
-  uint32_t* flist;   // ... those chunks (count ctl[kLcFall])
-  // per piece (index j: pieces of chunk i are lpo[i] .. lpo[i] + lnp[i] - 1), pcap of each
-  uint32_t* pbeg;    // first byte
-  uint32_t* pcnt;    // ids (0 once absorbed by a window)
-  uint32_t* pchunk;  // its chunk
-  uint32_t* pflag;   // kLpAlive | kLpConf
-  uint32_t* pprev;   // previous / next live piece of the chunk (kLpNone at the ends)
-  uint32_t* pnext;
-  uint32_t* pid;     // [n_bytes] a live piece's ids from its first byte's position on, then holes
-                     // (kLpHole) up to the next live piece
-  uint32_t* wlist;   // big windows of the current round: (head, last) piece pairs
-  uint32_t* jlist[2];  // junctions (their right piece) to check in an even / odd round (r > 0)
-  uint32_t* clist;   // pieces whose left junction conflicts (this round)
-  uint32_t* hlist;   // window heads (this round)
-  uint32_t* pseen;   // the last round r > 0 that checked the piece's left junction (a piece can be
-                     // listed twice: after one window and as the head of another)
-  int64_t* ctl;      // kLcWords counters
-  int64_t lcap, pcap;
-};
-
 __device__ __forceinline__ int64_t lp_count(const int64_t* p, int64_t cap) {
   const int64_t v = *p;
   return v < cap ? (v < 0 ? 0 : v) : cap;

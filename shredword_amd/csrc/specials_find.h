@@ -33,22 +33,6 @@ namespace sw {
 constexpr int kSpMaxLen = 64;     // the longest special the device finder takes (longer: host finder)
 constexpr int kSpMaxFirstSwar = 4;  // distinct first bytes compared by SWAR (more: a bit set in LDS)
 
-// the tokenizer's specials on the device (sw_encoder_set_specials)
-struct SpTab {
-  const uint8_t* bytes;  // every special's bytes, concatenated
-  const int32_t* off;    // [n + 1]
-  const int32_t* ids;    // [n]
-  const int32_t* list;   // the non-empty specials grouped by first byte, dict order within a group
-  const int32_t* first;  // [257]: first byte b's group is list[first[b] .. first[b + 1])
-  uint32_t filt[8];      // the first-byte set
-  uint32_t fb;           // the distinct first bytes, one per byte (n_first <= kSpMaxFirstSwar)
-  int32_t n_first;
-  int32_t max_len;
-  int32_t n;
-  const uint32_t* img;   // the table as k_sp_find stages it in LDS (layout above sft_len)
-  int32_t img_words, o_first, o_rec, o_tag, o_words;
-};
-
 struct SpFind {
   const uint8_t* bytes;
   int64_t n_bytes;

@@ -260,6 +260,30 @@ def test_random_wellformed_tables(seed):
     assert_same(gpu_encode(t, buf, off), oracle_encode(merges, buf, off, "none"))
 
 
+def test_pairs_with_the_empty_entrys_tag():
+    """The quotient table's empty entries carry tag 0xFFFF, and so do the byte pairs (32, 151) and
+    (246, 181) under the first draw of the builder's constants (tests/test_pairtable.py): their
+    merges must still fire, in every merge bucket (3..40 bytes) and on the long paths.  Each string
+    ends in a lone 0x41, so no chunk is a single token that the whole-chunk table would answer."""
+    merges = {(32, 151): 256, (246, 181): 257, (256, 257): 258}
+    r = random.Random(5)
+    units = [b"\x20\x97", b"\xf6\xb5", b"\x41"]
+
+    def make(n):
+        s = b""
+        while len(s) < n - 1:
+            s += r.choice(units if len(s) < n - 2 else units[2:])
+        return s + b"\x41"
+
+    datas = [make(n) for n in range(3, 41) for _ in range(8)] + [make(100), make(3000)]
+    buf, off = pack(datas)
+    t = sa.Tokenizer()
+    t.merges = merges
+    assert _lib.lib().sw_encoder_get_info(t._encoder(), _lib.SW_INFO_IDS16) == 1
+    t.pattern = PAT_STR["none"]
+    assert_same(gpu_encode(t, buf, off), oracle_encode(merges, buf, off, "none"))
+
+
 def test_wide_ids_table():
     """Ids > 65535 (e.g. vocabularies past 64k): the 16-byte-slot table path."""
     base = load_model_merges("bl32k.model")
