@@ -759,7 +759,7 @@ hipError_t launch_classify_pair(sw_encoder* h, hipStream_t st, const EncArgs& a,
     const RedoList redo{count, tiles};  // (its count zeroed by k_edges)
     const uint32_t* edge = h->ws.d_edge;
     uint32_t* pbits = (uint32_t*)h->ws.d_pbits.get();
-    hipLaunchKernelGGL(k_split_classify<kSp>, gc, b, 0, st, a, *pg, pattern, edge, pbits, redo);
+    hipLaunchKernelGGL(k_split_classify<kSp>, gc, b, 0, st, ScArgs{a, *pg, pattern, edge, pbits, redo});
     if (c1 && (e = hipEventRecord(c1, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_split_redo<kSp>, gr, b, 0, st, a, *pg, pattern, edge, pbits, redo);
   } else {

@@ -861,6 +861,17 @@ struct EncArgs {
   SpArgs sp;                 // special-token occurrences (sp.n == 0: none)
 };
 
+// Diagnostic builds only (make variant DEFS=-DSW_DIAG_PHASES=k; timing and counters, wrong ids): the
+// tile path of k_split_classify cut after phase k -- 1 staging + string starts, 2 class masks,
+// 3 rules + bitmap (the tile then goes on with no chunks, so that every count the later kernels
+// read is written, as zero); 4 chunk-start list (no chunk settled); 5 lookups (every other chunk
+// settled as token 0: no dedupe, no queue).  The differences between the builds' counters are the
+// phases' (DESIGN.md 4.1).  0: the real kernel.
+#ifndef SW_DIAG_PHASES
+#define SW_DIAG_PHASES 0
+#endif
+constexpr int kDiagPhases = SW_DIAG_PHASES;
+
 #ifdef SW_STAMPS
 #define SW_STAMP(k)                                                                 \
   do {                                                                              \
@@ -1145,7 +1156,8 @@ __device__ __forceinline__ void classify_chunks(const EncArgs& a, int64_t tile, 
   //    point their slot at the first occurrence's result, the others are queued for the merge
   //    kernels and counted per length bucket (lane b: bucket b).
   int32_t* dst = a.scratch + t0;
-  const int rounds = (C + 63) >> 6;
+  const int C_out = kDiagPhases == 4 ? 0 : C;  // (the chunks the later kernels hear of)
+  const int rounds = (C_out + 63) >> 6;
 #ifdef SW_DIAG_NO_LOOKUP  // (diagnostic, wrong ids: every multi-byte chunk "hits" token 0, no memory access)
   const bool use_table = false;
 #else
@@ -1184,6 +1196,7 @@ __device__ __forceinline__ void classify_chunks(const EncArgs& a, int64_t tile, 
       for (int u = 0; u < kLookRounds; ++u) {
         const int k = ((r0 + u) << 6) + lane;
         const bool valid = k < C;
+        if (kDiagPhases == 5 && tok[u] == kInf) tok[u] = 0u;
         const bool queued = valid && tok[u] == kInf;
         if (valid && !queued && (!kSp || tok[u] != kSpDone)) SW_STNT(&dst[k], (int32_t)tok[u]);
         const uint64_t mq = __ballot(queued);
@@ -1264,7 +1277,7 @@ __device__ __forceinline__ void classify_chunks(const EncArgs& a, int64_t tile, 
   // 4. per-bucket counts of the queued chunks (k_scan -> k_scatter)
   if (lane < kNumBuckets) a.bcnt[(int64_t)lane * a.n_tiles + tile] = bcount;
   if (lane == 0) {
-    a.tile_slots[tile] = (uint32_t)C;
+    a.tile_slots[tile] = (uint32_t)C_out;
     a.tile_nref[tile] = (uint32_t)nref;
   }
   SW_STAMP(2);
@@ -1277,7 +1290,7 @@ __device__ __forceinline__ void classify_chunks(const EncArgs& a, int64_t tile, 
   for (int64_t s = s_first_now + lane; s < a.n_str; s += 64) {
     const int64_t p = a.str_off[s];
     if (p >= t1) break;
-    int lo = 0, hi = C;  // first chunk with start >= p
+    int lo = 0, hi = C_out;  // first chunk with start >= p
     const int lp = (int)(p - t0);
     while (lo < hi) {
       const int m = (lo + hi) >> 1;

@@ -56,8 +56,33 @@ struct Masks {
   uint32_t L, N, C, P, H, A, X, K1, K2;
 };
 
-// bit 7 of each byte lane of x -> 4 bits
-SW_HD inline uint32_t mm4(uint32_t x) { return ((x & 0x80808080u) * 0x00204081u) >> 28; }
+// v_dot4_u32_u8: the sum of the four byte products a_k * b_k, plus c
+SW_HD inline uint32_t dot4_u8(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_udot4(a, b, c, false);
+#else
+  for (int k = 0; k < 4; ++k) c += ((a >> (8 * k)) & 0xFFu) * ((b >> (8 * k)) & 0xFFu);
+  return c;
+#endif
+}
+
+// Bit gathers of one plane: bit B of byte k of x -> bit k, as one AND and one dot product with the
+// byte weights 1, 2, 4, 8 (v_dot4_u32_u8 issues at the rate of the 32-bit multiply of the usual
+// SWAR gather, half that of a plain instruction: DESIGN.md 4.1; it saves the shift and the OR).
+// The second word's weights are 16 .. 128 and the first word's sum is its accumulate operand, so
+// two words give a finished mask byte.  The result is left shifted by B (the isolated bits are
+// worth 1 << B each); the caller shifts once per mask.
+template <int B>
+SW_HD inline uint32_t bits8_raw(uint32_t lo, uint32_t hi) {
+  return dot4_u8(hi & (kLane0 << B), 0x80402010u, dot4_u8(lo & (kLane0 << B), 0x08040201u, 0u));
+}
+// bit B of each of the 32 bytes of the words w(0) .. w(7) -> 32 bits
+template <int B, class W>
+SW_HD inline uint32_t bits32(const W& w) {
+  const uint32_t lo = bits8_raw<B>(w(0), w(1)) | (bits8_raw<B>(w(2), w(3)) << 8);
+  const uint32_t hi = bits8_raw<B>(w(4), w(5)) | (bits8_raw<B>(w(6), w(7)) << 8);
+  return (lo >> B) | ((hi >> B) << 16);
+}
 
 SW_HD inline uint64_t rev64(uint64_t x) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -116,8 +141,8 @@ SW_HD inline uint32_t perm_b32(uint32_t hi, uint32_t lo, uint32_t sel) {
 //   bit 7 L (0x41..0x4F, 0x61..0x6F)  bit 3 L (0x50..0x5A, 0x70..0x7A)  bit 6 N (0-9)
 //   bit 2 C (\n \r)                  bit 5 P (space)                     bit 1 H (\t \v \f)
 //   bit 4 A (apostrophe)
-// so that one multiply gathers two classes (bits 7 and 3 of each byte).  Bytes >= 0x80 get
-// garbage here; the caller clears them with the non-ASCII bits at mask level.
+// (the letters take two bits: their two column ranges are two products of a row set and a column
+// set).  Bytes >= 0x80 get garbage here; the caller clears them with the non-ASCII bits at mask level.
 SW_HD inline uint32_t ascii_class4(uint32_t x) {
   const uint32_t lo = x & 0x07070707u;
   const uint32_t pa = perm_b32(0xD8C8C8C8u, 0xC8C8C868u, lo);   // low nibble 0..7
@@ -127,8 +152,39 @@ SW_HD inline uint32_t ascii_class4(uint32_t x) {
   const uint32_t thi = perm_b32(0x08800880u, 0x40300006u, (x >> 4) & 0x07070707u);
   return tlo & thi;
 }
-// bits 7 and 3 of each byte lane of x -> 8 bits: bits 4..7 (bit 7s), bits 0..3 (bit 3s)
-SW_HD inline uint32_t mm8(uint32_t x) { return ((x & 0x88888888u) * 0x00204081u) >> 24; }
+
+// The eight bit planes of 32 bytes: w[i] = bytes 4i .. 4i + 3 on entry; on return bit k of w[b] =
+// bit b of byte k.  Every plane at once costs less than three single gathers: 16 v_perm_b32
+// bring byte 8q + r to byte lane q of word r (two 4 x 4 byte transposes), then three rounds of
+// block swaps (shift + v_bfi_b32, all four byte lanes at a time) transpose the 8 x 8 bit matrix
+// that the words' byte lanes q hold.
+SW_HD inline void bit_planes32(uint32_t (&w)[8]) {
+  uint32_t u[8];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {  // words g, g + 2, g + 4, g + 6 -> u[4g .. 4g + 3]
+    const uint32_t p0 = perm_b32(w[g + 2], w[g], 0x05010400u), p1 = perm_b32(w[g + 2], w[g], 0x07030602u);
+    const uint32_t q0 = perm_b32(w[g + 6], w[g + 4], 0x05010400u), q1 = perm_b32(w[g + 6], w[g + 4], 0x07030602u);
+    u[4 * g + 0] = perm_b32(q0, p0, 0x05040100u);
+    u[4 * g + 1] = perm_b32(q0, p0, 0x07060302u);
+    u[4 * g + 2] = perm_b32(q1, p1, 0x05040100u);
+    u[4 * g + 3] = perm_b32(q1, p1, 0x07060302u);
+  }
+  // bits b >= s of word r <-> bits b < s of word r + s, for s = 4, 2, 1
+  auto swap_blocks = [&](int s, uint32_t low) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      if (r & s) continue;
+      const uint32_t a = u[r], b = u[r + s];
+      u[r] = (a & low) | ((b << s) & ~low);
+      u[r + s] = ((a >> s) & low) | (b & ~low);
+    }
+  };
+  swap_blocks(4, 0x0F0F0F0Fu);
+  swap_blocks(2, 0x33333333u);
+  swap_blocks(1, 0x55555555u);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) w[r] = u[r];
+}
 
 // The class of a code point in one of the big single-class ranges of the most common non-ASCII
 // scripts, from registers; -1 when cp is outside them (the caller then reads the UCD tables: two
@@ -149,38 +205,37 @@ SW_HD inline int fast_class(uint32_t cp) {
 // bytes k .. k + 3 of those 40 (k <= 36).
 template <class Cls, class Bytes>
 SW_HD inline Masks classify(const Bytes& by, uint64_t ss, const Cls& cls, bool cl) {
-  // ASCII classes of the chunk's bytes (words 1..8): a class byte per byte (ascii_class4), two
-  // classes gathered per multiply
-  uint32_t L = 0, N = 0, C = 0, P = 0, H = 0, A = 0;
+  // ASCII classes of the chunk's bytes (words 1..8): a class byte per byte (ascii_class4; its
+  // bit 0 is free and takes "byte >= 0x80"), then the class bytes' bit planes (bit_planes32)
+  uint32_t t[8];
 #pragma unroll
-  for (int i = 1; i < 9; ++i) {
-    const uint32_t t = ascii_class4(by.word(i));
-    const int s = 4 * (i - 1);
-    const uint32_t l = mm8(t), nc = mm8(t << 1), ph = mm8(t << 2);
-    L |= ((l >> 4) | (l & 15u)) << s;
-    N |= (nc >> 4) << s;
-    C |= (nc & 15u) << s;
-    P |= (ph >> 4) << s;
-    H |= (ph & 15u) << s;
-    A |= mm4(t << 3) << s;
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t x = by.word(i + 1);
+    t[i] = ascii_class4(x) | ((x >> 7) & kLane0);
   }
+  bit_planes32(t);
+  uint32_t L = t[7] | t[3], N = t[6], C = t[2], P = t[5], H = t[1], A = t[4];
   // UTF-8: every lead byte of [pos - 4, pos + 32) checked on its own (strict: no overlongs,
   // surrogates or code points past U+10FFFF, not crossing a string start); the continuation
   // bytes of the valid ones make X, and the chunk's non-ASCII code points get their class
   uint64_t X = 0;
-  uint64_t hi40 = 0, ct40 = 0;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) hi40 |= (uint64_t)mm4(by.word(i)) << (4 * i);
+  uint64_t ct40 = 0;
+  // bit 7 of the 8 bytes of the words before and after the chunk: bits 0..3 word 0, 4..7 word 9
+  auto ends8 = [&](uint32_t u0, uint32_t u9) -> uint64_t {
+    const uint32_t e = bits8_raw<7>(u0, u9) >> 7;
+    return (uint64_t)(e & 15u) | ((uint64_t)(e >> 4) << 36);
+  };
+  const uint64_t hi40 = ((uint64_t)t[0] << 4) | ends8(by.word(0), by.word(9));
   {  // (the ASCII classes of bytes >= 0x80 were garbage)
     const uint32_t asc = ~(uint32_t)(hi40 >> 4);
     L &= asc; N &= asc; C &= asc; P &= asc; H &= asc; A &= asc;
   }
   if (hi40) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      const uint32_t x = by.word(i), h7 = (x ^ kLane7) & kLow7;  // (bytes >= 0x80, less 0x80)
-      ct40 |= (uint64_t)mm4(in7(h7, 0x00, 0x3F) & x & kLane7) << (4 * i);
-    }
+    auto ct4 = [&](int i) -> uint32_t {  // (bytes >= 0x80, less 0x80, below 0x40)
+      const uint32_t x = by.word(i);
+      return in7(x & kLow7, 0x00, 0x3F) & x;
+    };
+    ct40 = ((uint64_t)bits32<7>([&](int i) -> uint32_t { return ct4(i + 1); }) << 4) | ends8(ct4(0), ct4(9));
     // one lead: its continuation bytes (0 if invalid), its code point (kInvalidCp if it needs
     // no class: invalid, or before the chunk)
     auto lead = [&](int k, uint64_t* tail_out) -> uint32_t {

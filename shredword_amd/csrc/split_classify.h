@@ -450,20 +450,26 @@ __device__ __forceinline__ void split_classify_tile(const EncArgs& a, const PbAr
   __builtin_amdgcn_s_waitcnt(0);
   SW_STAMP(12);
 #endif
-  const FSrc src{GSrc{g, a.n_tiles, n_chunks, cl}, &sm, c0, t0, n_chunks};
+  // string starts of the 32 bytes from the lane's chunk + d on (d in [-kScSsPre, 96]: always staged,
+  // so no search of str_off as FSrc::ss_at would fall back to)
+  auto ss_rel = [&](int d) -> uint32_t {
+    const int r = kScSsPre + 32 * lane + d, wi = r >> 5;
+    return (uint32_t)(((uint64_t)sm.ss[wi] | ((uint64_t)sm.ss[wi + 1] << 32)) >> (r & 31));
+  };
+  static_assert(kScSsPre + 32 * 63 + 96 + 32 <= kScSsWords * 32 && kScSsPre >= 16, "ss_rel stays inside the staged words");
   // 3. this lane's chunk: class masks (to LDS, where the rules read them: nothing is held in
   //    registers across the rare walk of psb::carries, which would otherwise cost ~60 VGPRs)
   uint32_t r = 0;
   bool unresolved = false;  // (a walk left the tile: the tile goes to k_split_redo)
-  if (pattern == 2) {  // the chunks are the strings
-    if (c < n_chunks) r = src.ss(c);
+  if (kDiagPhases == 1) {
+  } else if (pattern == 2) {  // the chunks are the strings
+    if (c < n_chunks) r = ss_rel(0);
   } else {
     {
       psb::Masks m1{};
       if (c < n_chunks) {
         const MixBytes by{rw, s_win + (kScPre / 4 - 1) + 8 * lane};  // bytes [t0 + 32 lane - 4, +40)
-        const int64_t p = 32 * c;
-        const uint64_t s = (uint64_t)src.ss_at(p - 4) | ((uint64_t)(src.ss_at(p + 28) & 0xFFu) << 32);
+        const uint64_t s = (uint64_t)ss_rel(-4) | ((uint64_t)(ss_rel(28) & 0xFFu) << 32);
         m1 = psb::classify(by, s, UcdClass{}, cl);
       }
       const int k = lane + 1;
@@ -475,9 +481,8 @@ __device__ __forceinline__ void split_classify_tile(const EncArgs& a, const PbAr
     auto col = [&](int k) {
       return psb::Masks{sm.m[0][k], sm.m[1][k], sm.m[2][k], sm.m[3][k], sm.m[4][k], sm.m[5][k], sm.m[6][k], sm.m[7][k], sm.m[8][k]};
     };
-    if (c < n_chunks) {
-      const int64_t p = 32 * c;
-      const uint64_t ssw = (uint64_t)src.ss_at(p - 16) | ((uint64_t)src.ss_at(p + 16) << 32);
+    if (kDiagPhases != 2 && c < n_chunks) {
+      const uint64_t ssw = (uint64_t)ss_rel(-16) | ((uint64_t)ss_rel(16) << 32);
       uint32_t need = 0;
       r = psb::rules(col(lane), col(lane + 1), col(lane + 2), ssw, cl, psb::Carry{}, &need);
       if (lane == 0) {  // (k_edges has lane 0's word, from the previous tile's masks)
@@ -486,6 +491,7 @@ __device__ __forceinline__ void split_classify_tile(const EncArgs& a, const PbAr
       }
       if (need) {
         if constexpr (kRedo) {
+          const FSrc src{GSrc{g, a.n_tiles, n_chunks, cl}, &sm, c0, t0, n_chunks};
           const psb::Carry cy = psb::carries(src, c, need);
           asm volatile("" ::: "memory");  // (the masks re-read from LDS, not kept live across the walk)
           r = psb::rules(col(lane), col(lane + 1), col(lane + 2), ssw, cl, cy, &need);
@@ -525,20 +531,38 @@ __device__ __forceinline__ void split_classify_tile(const EncArgs& a, const PbAr
   else if (a.n_bytes <= t1 + 32) rel_end = (int)(a.n_bytes - t0);
   else rel_end = kRelEndLong;
   wave_sync_mem();  // (the masks' LDS becomes the chunk-start list)
-    classify_chunks<kSp>(a, tile, s_win + kScPre / 4, sh->cstart, s_qbuf, r, rel_end, s_first, -1, -1);
+    classify_chunks<kSp>(a, tile, s_win + kScPre / 4, sh->cstart, s_qbuf,
+                         kDiagPhases >= 1 && kDiagPhases <= 3 ? 0u : r, rel_end, s_first, -1, -1);
 }
 
+// k_split_classify's arguments, as the one struct its kernel-argument segment holds
+struct ScArgs {
+  EncArgs a;
+  PbArgs g;
+  int pattern;
+  const uint32_t* edge;
+  uint32_t* bits32;
+  RedoList redo;
+};
+
+// The arguments are read through the pointer to the kernel-argument segment, each field where the
+// tile path uses it, and not as the by-value parameter: the compiler loads every field of a
+// by-value argument that the kernel uses in its entry block (some 60 scalar registers here, live
+// through the class masks and the rules), and the register allocator then moves them, and the
+// rules' 64-bit masks, in and out of vector lanes (235 spilled scalars, 946
+// v_readlane / v_writelane of 4,298 vector instructions, before).
 template <bool kSp>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7, 7)))
-k_split_classify(EncArgs a, PbArgs g, int pattern, const uint32_t* edge, uint32_t* bits32, RedoList redo) {
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7, 7))) k_split_classify(ScArgs by_value) {
   __shared__ __attribute__((aligned(16))) uint32_t s_win_all[kWaves][kScWinWords];
   __shared__ ScSharedT<kScCsCap> s_sh_all[kWaves];
   __shared__ uint16_t s_qb_all[kWaves][kQBuf];
+  (void)by_value;
+  const ScArgs& k = *(const ScArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   const int wv = wave_in_block_s();
   const int64_t tile = (int64_t)blockIdx.x * kWaves + wv;
-  if (tile < a.n_tiles)
-    split_classify_tile<kSp, false>(a, g, pattern, edge, bits32, tile, s_win_all[wv], &s_sh_all[wv], s_qb_all[wv],
-                                    redo);
+  if (tile < k.a.n_tiles)
+    split_classify_tile<kSp, false>(k.a, k.g, k.pattern, k.edge, k.bits32, tile, s_win_all[wv], &s_sh_all[wv],
+                                    s_qb_all[wv], k.redo);
 }
 
 // the tiles k_split_classify listed (a run crossing the tile: walks over global memory), one wave
