@@ -304,10 +304,14 @@ double sw_encoder_last_kernel_ms(const sw_encoder* h);
  * bitmap): the pipeline's dominant kernel, timed by HIP events on the launch stream */
 double sw_encoder_last_classify_ms(const sw_encoder* h);
 
-/* What the last sw_encode_device launch did (synchronises on it): out4[0] chunks, out4[1] chunks
- * that went to the merge loop (references to a merge result: not a single byte, not in the
- * whole-chunk table), out4[2] distinct ones actually merged (after the in-launch dedupe),
- * out4[3] tiles.  For reports; outside any timed region. */
+/* What the last sw_encode_device launch did (synchronises on it): out4[0] chunks (a special-token
+ * occurrence is one chunk), out4[1] chunks that went to the merge loop (references to a merge
+ * result: not a single byte, not a special-token occurrence, not in the whole-chunk table; chunks
+ * over 32 bytes included), out4[2] the merge loops actually run for chunks of at most 32 bytes
+ * (after the in-launch dedupe: their distinct byte strings, plus the repeats that found their
+ * line of the dedupe table full; chunks over 32 bytes take the long-chunk path and are left out),
+ * out4[3] tiles (ceil(n_bytes / 2048)).  All zero but out4[3] after a launch of 0 bytes.  For
+ * reports and tests; outside any timed region. */
 int32_t sw_encoder_last_counts(sw_encoder* h, int64_t* out4);
 
 /* Diagnostic builds only (compiled with -DSW_STAMPS): device cycles summed over workgroups,
